@@ -10,8 +10,8 @@ up to --chunk sites: main + group + deep kernels).  By default the genome is
 divided by 8 / N (--c4-scale auto): every GPU holds one eighth of GRCh38
 (3.86e8 sites, about 143 GB of packed reads in HBM), so N = 8 scores the whole
 3.09e9-site genome of configs[3] in one step and N = 1, 2, 4 the same
-per-GPU share (weak scaling: per-GPU work fixed).  A secondary line,
-"strong_scaling", times the genome / 16 at every N (total work fixed).
+per-GPU share (weak scaling: per-GPU work fixed).  With --full a secondary
+line, "strong_scaling", times the genome / 16 at every N (total work fixed).
 Workload shard: --sites sites per rank per step (weak scaling; the C2/C3/C5
 depth runs).  Inputs are generated on the device before timing; the timed
 region contains only scoring.
@@ -25,10 +25,16 @@ directly as ``bench.py --gpus N``: the parent then starts N fresh rank
 processes itself before anything touches the GPU, stays GPU-free, and relays
 rank 0's line.
 
-Extra fields, all measured by rank 0 after the timed region at EVERY N (so
-each line of a 1/2/4/8-GPU scaling run carries them): "roofline" (the kernel
-with the most time, HIP events over the timed region's launches, algorithmic
-bytes 4 B/read + 16 B/site per launch; "traffic" and "valu" from rocprofv3
+A plain run sets up, warms up, times --steps steps and prints the line with
+"roofline" (the kernel with the most time, HIP events over the timed region's
+launches, algorithmic bytes 4 B/read + 16 B/site per launch).  --dump-outputs
+DIR also writes what the last timed step computed (dump_outputs below); the
+inputs depend only on the arguments, so two builds can be compared output for
+output.
+
+--full adds the measurements that take runs of their own, all by rank 0 after
+the timed region at EVERY N (so each line of a 1/2/4/8-GPU scaling run
+carries them): the roofline's "traffic" and "valu" (rocprofv3
 --pmc passes over a child scoring rank 0's own first launches of this N),
 "cpu_baseline" (the real reference glf_somatic compiled from source,
 oracle/_ref/ref_harness, 1 core, on a bounded sample of the same synthetic
@@ -570,6 +576,41 @@ def synth_pieces(ctx, pkg, args, pieces, dev):
             "n_reads": (T, N), "n_sites": S}
 
 
+DUMP_SEED = 0xD0E5                 # --dump-outputs: seed of the site sample
+DUMP_SCORE_SITES = 1 << 22         # scores kept over all launches of the step (8 B each: 32 MiB)
+DUMP_CALL_ROWS = 1 << 17           # emitted calls kept (13 float64 each: 13 MiB)
+
+
+def dump_outputs(path, pkg, prefix, last, batches, score, calls, ncalls, cap):
+    """--dump-outputs: what a caller of the timed path holds after the last
+    timed step, as float64 .npy files (every value is an integer below 2^53,
+    so the conversion is exact): `score_l<k>` the somatic scores of launch k
+    of that step (all sites, or a fixed seeded sample of them in site order
+    when the step has more than DUMP_SCORE_SITES), `n_calls` and `calls` the
+    emitted-call counter and records the step's last launch left in the shared
+    call buffer (the device path appends them in arbitrary order: sorted by
+    site here; one row per call, the fields of ss_call_t without its pad)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    per = max(1, DUMP_SCORE_SITES // len(last))
+    for k in last:
+        n = batches[k]["n_sites"]
+        s = score[k][:n]
+        if n > per:
+            idx = np.unique(np.random.default_rng(DUMP_SEED + k).integers(0, n, per))
+            s = s[torch.from_numpy(idx).to(s.device)]
+        np.save(os.path.join(path, f"{prefix}score_l{k}.npy"), s.cpu().numpy().astype(np.float64))
+    nc = int(ncalls.cpu().numpy().view(np.uint32)[0])
+    np.save(os.path.join(path, f"{prefix}n_calls.npy"), np.array([nc], np.float64))
+    if nc <= cap:                  # past the capacity the records kept are an arbitrary subset
+        c = calls[: nc * pkg.SS_CALL_DTYPE.itemsize].cpu().numpy().view(pkg.SS_CALL_DTYPE)
+        c = c[np.argsort(c["site"], kind="stable")][:DUMP_CALL_ROWS]
+        cols = [f for f in pkg.SS_CALL_DTYPE.names if f != "pad"]
+        np.save(os.path.join(path, f"{prefix}calls.npy"),
+                np.stack([c[f].astype(np.float64) for f in cols], axis=1) if len(c)
+                else np.zeros((0, len(cols)), np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -604,15 +645,26 @@ def main():
     ap.add_argument("--no-host-fed", action="store_true", help="skip the host-fed (PCIe-inclusive) sub-line")
     ap.add_argument("--host-fed-sites", type=int, default=1 << 22,
                     help="sites per ss_score_batch_host call of the host-fed sub-line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements: the strong-scaling line, the "
+                         "live rocprofv3 counter passes, the host-fed sub-line and the CPU baselines (each can "
+                         "still be switched off by its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (scores per launch, the emitted calls of its "
+                         "last launch) as DIR/<name>.npy; a fixed seeded sample where an array is large")
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child(args)
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu = args.no_pmc = args.no_host_fed = True
+        args.strong_steps = 0
 
     bad = [k for k in REFUSED_ENV if os.environ.get(k)]
     if bad:
         sys.exit(f"bench.py: refusing to time with tuning/diagnostic variables set: {', '.join(bad)}")
-    if args.gpus < 1:
-        sys.exit("bench.py: --gpus must be >= 1")
+    if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --gpus and --steps must be >= 1, --warmup >= 0")
     if (args.c4_scale is not None and args.c4_scale < 1) or args.chunk < 1 or args.strong_scale < 1:
         sys.exit("bench.py: --c4-scale, --strong-scale and --chunk must be >= 1")
     if "WORLD_SIZE" not in os.environ:
@@ -712,6 +764,9 @@ def main():
     ctx.set_kernel_timing(False)
     ctx.check()
     elapsed = t1 - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pkg, f"rank{rank}_" if world > 1 else "",
+                     per_step if c4 else [(args.steps - 1) % len(batches)], batches, score, calls, ncalls, cap)
     # per-kernel HIP-event durations of the logged launches (the first 4096);
     # the roofline is quoted for the kernel with the most time
     klog = {k: ctx.kernel_time_log(k) for k in ("main", "wide", "deep")}
@@ -738,7 +793,7 @@ def main():
     # that contig; shard: batch 0, synth shard = rank)
     sample = depth_scaled(2_000_000, args.lt, args.ln) if args.cpu_sample is None else args.cpu_sample
     pre, cpu_shard = None, 0
-    if batches and batches[0]["first"] == 0:
+    if not args.no_cpu and batches and batches[0]["first"] == 0:
         d0 = batches[0]
         n0 = d0["pieces"][0][2] if c4 else d0["n_sites"]       # the first contig's sites in that launch
         sample = min(sample, n0)

@@ -19,9 +19,9 @@ def test_bench_json_contract():
     fields, strong scaling (a fixed --c4-scale), the roofline of the timed
     launches, the strong-scaling line and the 1-core reference baseline with
     its parity spot check."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--c4-scale", "4096", "--steps", "2",
-                        "--warmup", "1", "--cpu-sample", "20000", "--strong-scale", "8192", "--strong-steps", "2",
-                        "--host-fed-sites", "262144"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--c4-scale", "4096",
+                        "--steps", "2", "--warmup", "1", "--cpu-sample", "20000", "--strong-scale", "8192",
+                        "--strong-steps", "2", "--host-fed-sites", "262144"],
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads(p.stdout.strip().splitlines()[-1])
@@ -64,8 +64,8 @@ def test_bench_json_contract():
 def test_bench_shard_workload_depth_baseline():
     """--workload shard (the C2/C3/C5 depth runs): weak scaling, and the CPU
     baseline is taken at the run's own depth with its parity spot check."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "shard", "--lt", "500",
-                        "--ln", "500", "--sites", "65536", "--steps", "2", "--warmup", "1", "--no-pmc",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "shard",
+                        "--lt", "500", "--ln", "500", "--sites", "65536", "--steps", "2", "--warmup", "1", "--no-pmc",
                         "--cpu-sample", "3000"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads(p.stdout.strip().splitlines()[-1])
@@ -74,6 +74,49 @@ def test_bench_shard_workload_depth_baseline():
     assert r["roofline"]["kernel"] == "ss_score_triage+ss_score_triage_deep+ss_score_main"
     cb = r["cpu_baseline"]
     assert "500.0xT/500.0xN" in cb["sample"] and cb["parity_vs_gpu"] is True
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dumped_outputs(pkg, oracle, tmp_path):
+    """A plain run (no --full) times its steps and nothing else: the line has
+    the headline fields and the HIP-event roofline, none of the secondary
+    measurements.  --dump-outputs writes the last step's scores and emitted
+    calls as float64 .npy files; the scores of the first contig equal the CPU
+    oracle's on the same synthetic sites (the inputs depend on the arguments
+    alone), and the calls are the emitted sites in site order."""
+    import numpy as np
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--c4-scale", "4096",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    r = json.loads(p.stdout.strip().splitlines()[-1])
+    assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["unit"] == "sites/s" and r["higher_is_better"] is True
+    genome = sum(-(-length // 4096) for length in GRCH38)
+    assert r["ranks"][0]["sites"] == 3 * genome
+    assert abs(r["value"] - genome / (r["ms_per_step"] * 1e-3)) / r["value"] < 1e-3
+    for k in ("cpu_baseline", "cpu_baseline_all_cores", "host_fed", "strong_scaling"):
+        assert k not in r, k
+    rf = r["roofline"]
+    assert 0 < rf["frac"] < 1 and rf["launches_timed"] == 3 and rf["traffic"] is None and "valu" not in rf
+    files = sorted(f.name for f in out.iterdir())
+    assert files == ["calls.npy", "n_calls.npy", "score_l0.npy"]
+    arrs = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float64 for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64e6
+    score = arrs["score_l0"]
+    assert score.shape == (genome,)
+    n0 = -(-GRCH38[0] // 4096)                     # chr1 from position 0: synth shard 0
+    h = pkg.synth_batch_host(pkg.Synth.default(60, 30, seed=0x5EED5A1DC0FFEE01, shard=0), 0, n0)
+    want, want_calls, _ = oracle.Oracle().score_batch(h.ref, h.off_tumor, h.off_normal, h.reads_tumor,
+                                                      h.reads_normal, want_glf=False)
+    assert (score[:n0] == want).all()
+    calls, n_calls = arrs["calls"], int(arrs["n_calls"][0])
+    assert calls.shape == (n_calls, 13) and n_calls > len(want_calls) > 0
+    assert (np.diff(calls[:, 0]) > 0).all()
+    k = len(want_calls)
+    assert (calls[:k, 0] == want_calls["site"]).all() and (calls[:k, 1] == want_calls["somatic_score"]).all()
+    assert (calls[:, 1] == score[calls[:, 0].astype(np.int64)]).all()
 
 
 # ---------------------------------------------------------------- CPU: launcher
@@ -137,7 +180,8 @@ def test_bench_c4_ranks_self_spawned_gloo(gpus):
     fields: the reference CPU baseline (rank 0, with its parity check), the
     PMC traffic of rank 0's own launches of this N, and the host-fed rate."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--backend", "gloo",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--backend",
+                        "gloo",
                         "--c4-scale", "8192", "--steps", "2", "--warmup", "1", "--strong-scale", "16384",
                         "--strong-steps", "2", "--cpu-sample", "20000", "--host-fed-sites", "65536"],
                        env=env, capture_output=True, text=True, timeout=600)

@@ -14,7 +14,7 @@ for V in "$@"; do
   PMC="--no-pmc"
   [ $first -eq 1 ] && PMC=""
   first=0
-  SNIPER_AMD_LIB=$L timeout -k 10 300 python "$R/bench.py" --workload shard --no-cpu $PMC --steps 5 --warmup 2 \
+  SNIPER_AMD_LIB=$L timeout -k 10 300 python "$R/bench.py" --full --workload shard --no-cpu $PMC --steps 5 --warmup 2 \
       --lt ${C5_LT:-500} --ln ${C5_LN:-500} --sites ${C5_SITES:-1048576} > "$O/$V.json" 2> "$O/$V.err" \
       || { echo "$V failed"; tail -5 "$O/$V.err"; exit 1; }
   python3 - "$O/$V.json" "$V" <<'PY'

@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd "$R"
-timeout -k 10 600 python bench.py "$@" > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 600 python bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err"
 cat "$O/bench.json"
 cd /tmp
 export TMPDIR=/tmp
