@@ -290,6 +290,57 @@ int    ss_kernel_time_log(ss_ctx_t *ctx, double *ms, int cap);
 #define SS_KT_ALL  3
 int    ss_kernel_time_log_k(ss_ctx_t *ctx, int kernel, double *ms, int cap);
 
+/* ---- BGZF inflation -----------------------------------------------------------
+ * BGZF members (the BAM container: gzip members of at most 64 KiB, SAM spec
+ * 4.1) inflated on the GPU, one wave per member, so a BAM can be decompressed
+ * without host cores (the read path of samtools-0.1.6 bgzf.c:488).  A handle
+ * is independent of ss_ctx_t: it holds no model tables, only a stream and
+ * device staging buffers.
+ *
+ * Per-member statuses.  A member that fails has its output span zeroed. */
+typedef struct ss_inflate ss_inflate_t;
+#define SS_INF_OK        0
+#define SS_INF_E_STREAM  1   /* invalid or truncated DEFLATE data                  */
+#define SS_INF_E_SIZE    2   /* decoded length != ISIZE, or ISIZE != the out span  */
+#define SS_INF_E_CRC     3   /* CRC-32 of the output != trailer                    */
+
+int  ss_inflate_create(int device, uint32_t max_members, ss_inflate_t **out);
+void ss_inflate_destroy(ss_inflate_t *h);
+/* Member i is comp[comp_off[i] .. comp_off[i+1]): raw DEFLATE data followed by
+ * the 8-byte gzip trailer (CRC32, ISIZE), i.e. what follows the gzip header.
+ * Its output goes to out[out_off[i] .. out_off[i+1]); nothing outside that
+ * span is written, whatever the data holds.  Device pointers, asynchronous on
+ * `stream` (a hipStream_t, NULL = default stream).  n > max_members is
+ * SS_E_INVAL.  The offsets are device memory, so they are checked on the
+ * device: a member whose offsets decrease, with more than 64 KiB + 8 input
+ * bytes or more than 64 KiB of output, gets SS_INF_E_STREAM and is neither
+ * read nor written. */
+int  ss_inflate_members_device(ss_inflate_t *h, const uint8_t *comp, const uint64_t *comp_off,
+                               uint32_t n, uint8_t *out, const uint64_t *out_off,
+                               uint32_t *status, void *stream);
+/* Host pointers: H2D on the handle's own stream, kernel, D2H, synchronous.
+ * Arrays from ss_host_alloc are copied without staging.  Offsets that
+ * decrease or a member of more than 64 KiB + 8 input bytes or 64 KiB of output
+ * are SS_E_INVAL; a bad member is a status, not a failure of the call. */
+int  ss_inflate_members_host(ss_inflate_t *h, const uint8_t *comp, const uint64_t *comp_off,
+                             uint32_t n, uint8_t *out, const uint64_t *out_off, uint32_t *status);
+/* The same decoder run on the calling thread (no GPU): same statuses, same bytes. */
+int  ss_inflate_members_cpu(const uint8_t *comp, const uint64_t *comp_off, uint32_t n,
+                            uint8_t *out, const uint64_t *out_off, uint32_t *status);
+/* Waits for the handle's stream.  Debug build: SS_E_CORRUPT if a guard band
+ * around one of the handle's device buffers was overwritten (ss_inflate_destroy
+ * reports the same on stderr). */
+int  ss_inflate_check(ss_inflate_t *h);
+/* Cut BGZF file bytes into members.  In the file a gzip header lies between
+ * two members' data, so the members are not contiguous: member i's DEFLATE
+ * data + trailer is file[comp_span[2i] .. comp_span[2i+1]) (comp_span holds
+ * 2 * cap entries), and its output offset is out_off[i] (cap + 1 entries, the
+ * prefix sum of ISIZE).  Stops at the first incomplete member or after cap
+ * members; *consumed says where.  SS_E_INVAL on a bad gzip header, a member
+ * without the BC subfield or an ISIZE above 64 KiB. */
+int  ss_bgzf_scan(const uint8_t *file, size_t len, uint64_t *comp_span, uint64_t *out_off,
+                  uint32_t cap, uint32_t *n_members, size_t *consumed);
+
 #ifdef __cplusplus
 }
 #endif

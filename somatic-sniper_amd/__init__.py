@@ -35,12 +35,14 @@ import numpy as np
 __all__ = [
     "Params", "Synth", "Batch", "Context", "SniperError", "library_path", "load_library",
     "synth_batch_host", "model_check", "pack_read", "SS_GLF_DTYPE", "SS_CALL_DTYPE", "EXPORTED_SYMBOLS",
+    "Inflater", "bgzf_scan", "inflate_cpu",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 SS_OK, SS_E_INVAL, SS_E_HIP, SS_E_NOMEM, SS_E_TABLES, SS_E_CAPACITY, SS_E_NODEV = 0, -1, -2, -3, -4, -5, -6
 SS_E_CORRUPT = -7
+SS_INF_OK, SS_INF_E_STREAM, SS_INF_E_SIZE, SS_INF_E_CRC = 0, 1, 2, 3   # per-member inflate statuses
 
 # every symbol include/sniper_amd.h declares
 EXPORTED_SYMBOLS = (
@@ -50,6 +52,8 @@ EXPORTED_SYMBOLS = (
     "ss_set_kernel_timing", "ss_last_kernel_ms", "ss_kernel_time_log", "ss_kernel_time_log_k", "ss_model_check", "ss_model_pinned",
     "ss_model_last_source",
     "ss_host_alloc", "ss_host_free",
+    "ss_inflate_create", "ss_inflate_destroy", "ss_inflate_members_device", "ss_inflate_members_host",
+    "ss_inflate_members_cpu", "ss_inflate_check", "ss_bgzf_scan",
 )
 
 
@@ -245,6 +249,14 @@ def load_library():
         lib.ss_model_last_source.restype = C.c_int
     lib.ss_kernel_time_log.argtypes = [vp, vp, C.c_int]
     lib.ss_kernel_time_log_k.argtypes = [vp, C.c_int, vp, C.c_int]
+    lib.ss_inflate_create.argtypes = [C.c_int, u32, C.POINTER(vp)]
+    lib.ss_inflate_destroy.argtypes = [vp]
+    lib.ss_inflate_destroy.restype = None
+    lib.ss_inflate_check.argtypes = [vp]
+    lib.ss_inflate_members_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
+    lib.ss_inflate_members_host.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+    lib.ss_inflate_members_cpu.argtypes = [vp, vp, u32, vp, vp, vp]
+    lib.ss_bgzf_scan.argtypes = [vp, C.c_size_t, vp, vp, u32, C.POINTER(u32), C.POINTER(C.c_size_t)]
     if hasattr(lib, "ss__test_poke_table"):         # test hook, not in the public header
         lib.ss__test_poke_table.argtypes = [vp, u64, C.c_int]
     if hasattr(lib, "ss__test_route_counts"):       # test hook, not in the public header
@@ -440,3 +452,137 @@ class Context:
     def sniper_glf2cns_fields(cns: int):
         """Decode a consensus word: (cns, cns2, rms_mapQ, cnsQ, cnsQ2) (sniper_maqcns.h:28)."""
         return cns >> 28, (cns >> 24) & 0xF, (cns >> 16) & 0xFF, (cns >> 8) & 0xFF, cns & 0xFF
+
+
+# --------------------------------------------------------------------------- BGZF inflation
+def _u8(data) -> np.ndarray:
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data, np.uint8)
+    return np.frombuffer(bytes(data) if not isinstance(data, (bytes, bytearray, memoryview)) else data, np.uint8)
+
+
+def bgzf_scan(data, cap: int | None = None):
+    """Cut BGZF file bytes into members (ss_bgzf_scan).  Returns (comp_span, out_off,
+    consumed): member i's DEFLATE data + trailer is data[comp_span[i, 0]:comp_span[i, 1]],
+    its output data_out[out_off[i]:out_off[i + 1]]; `consumed` is where the first
+    incomplete member (or the end of the data) starts."""
+    lib = load_library()
+    a = _u8(data)
+    if cap is None:
+        cap = a.size // 26 + 1                     # no member is shorter than header + 2 + trailer
+    span = np.zeros((cap, 2), np.uint64)
+    ooff = np.zeros(cap + 1, np.uint64)
+    n, used = C.c_uint32(), C.c_size_t()
+    _check(lib.ss_bgzf_scan(_ptr(a) or None, a.size, span.ctypes.data, ooff.ctypes.data, cap, C.byref(n),
+                            C.byref(used)), "ss_bgzf_scan")
+    return span[: n.value].copy(), ooff[: n.value + 1].copy(), int(used.value)
+
+
+def _pack_members(data):
+    """Members of BGZF file bytes, packed one after the other (the layout the
+    inflate calls take): (comp, comp_off, out_off)."""
+    a = _u8(data)
+    span, ooff, used = bgzf_scan(a)
+    if used != a.size:
+        raise ValueError(f"incomplete BGZF member at byte {used} of {a.size}")
+    lens = (span[:, 1] - span[:, 0]).astype(np.uint64)
+    coff = np.zeros(len(span) + 1, np.uint64)
+    np.cumsum(lens, out=coff[1:])
+    comp = np.empty(int(coff[-1]), np.uint8)
+    for i, (b, e) in enumerate(span):
+        comp[int(coff[i]):int(coff[i + 1])] = a[int(b):int(e)]
+    return comp, coff, ooff
+
+
+def _member_args(comp, comp_off, out_off, out):
+    comp = _u8(comp)
+    comp_off = np.ascontiguousarray(comp_off, np.uint64)
+    out_off = np.ascontiguousarray(out_off, np.uint64)
+    n = len(comp_off) - 1
+    if n < 0 or len(out_off) != n + 1:
+        raise ValueError("comp_off and out_off must have n + 1 entries")
+    if n and int(comp_off[-1]) > comp.size:
+        raise ValueError("comp_off passes the end of comp")
+    if out is None:
+        out = np.zeros(int(out_off[-1]) if n else 0, np.uint8)
+    elif n and int(out_off[-1]) > out.size:
+        raise ValueError("out_off passes the end of out")
+    return comp, comp_off, out_off, n, out, np.zeros(n, np.uint32)
+
+
+def inflate_members_cpu(comp, comp_off, out_off, out=None):
+    """ss_inflate_members_cpu: the shared decoder on the calling thread (no GPU)."""
+    comp, comp_off, out_off, n, out, status = _member_args(comp, comp_off, out_off, out)
+    _check(load_library().ss_inflate_members_cpu(_ptr(comp) or None, comp_off.ctypes.data, n, _ptr(out) or None,
+                                                 out_off.ctypes.data, _ptr(status) or None),
+           "ss_inflate_members_cpu")
+    return out, status
+
+
+def inflate_cpu(data):
+    """Inflate BGZF file bytes with the shared decoder on the host:
+    (bytes, status ndarray), as Inflater.inflate."""
+    out, status = inflate_members_cpu(*_pack_members(data))
+    return out.tobytes(), status
+
+
+class Inflater:
+    """BGZF members inflated on the GPU (ss_inflate_t): one wave per member."""
+
+    def __init__(self, device: int = 0, max_members: int = 4096):
+        self.lib = load_library()
+        h = C.c_void_p()
+        _check(self.lib.ss_inflate_create(device, max_members, C.byref(h)), "ss_inflate_create")
+        self.h = h
+        self.device = device
+        self.max_members = max_members
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.ss_inflate_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def inflate_members(self, comp, comp_off, out_off, out=None):
+        """Low-level call (ss_inflate_members_host): member i is
+        comp[comp_off[i]:comp_off[i+1]] (DEFLATE data + 8-byte trailer), its output
+        out[out_off[i]:out_off[i+1]].  Returns (out u8 ndarray, status u32 ndarray);
+        more than max_members members go in several calls."""
+        comp, comp_off, out_off, n, out, status = _member_args(comp, comp_off, out_off, out)
+        for a in range(0, n, self.max_members):
+            k = min(self.max_members, n - a)
+            _check(self.lib.ss_inflate_members_host(self.h, _ptr(comp) or None, comp_off[a:].ctypes.data, k,
+                                                    _ptr(out) or None, out_off[a:].ctypes.data,
+                                                    status[a:].ctypes.data), "ss_inflate_members_host")
+        return out, status
+
+    def inflate_device(self, comp, comp_off, n, out, out_off, status, stream=None):
+        """ss_inflate_members_device: torch CUDA tensors (or raw device addresses),
+        asynchronous on `stream`."""
+        def p(x):
+            return x if isinstance(x, int) else x.data_ptr()
+        sh = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        _check(self.lib.ss_inflate_members_device(self.h, p(comp), p(comp_off), n, p(out), p(out_off), p(status),
+                                                  sh), "ss_inflate_members_device")
+
+    def inflate(self, data):
+        """Scan BGZF file bytes, inflate every member on the GPU and return
+        (bytes, status ndarray): the concatenated output (a failed member's bytes
+        are zero) and one SS_INF_* status per member."""
+        out, status = self.inflate_members(*_pack_members(data))
+        return out.tobytes(), status
+
+    def check(self):
+        """Wait for the handle's stream; debug build: SS_E_CORRUPT if a guard band was overwritten."""
+        _check(self.lib.ss_inflate_check(self.h), "ss_inflate_check")

@@ -47,7 +47,11 @@
  * scoring, so the pileup restatement is testable on a host without a GPU; no
  * output records are written), SS_TIMING=1 (phase times on stderr),
  * SS_CONTIG_GROUPS (contig ranges pileup in parallel when both BAMs are
- * indexed, default 4; 1 keeps the single streaming walk).
+ * indexed, default 4; 1 keeps the single streaming walk),
+ * SS_BGZF_DEVICE (1: BGZF members are inflated on the first scoring GPU,
+ * SS_BGZF_DEVICE_BATCH (default 256) members per call, through the reader's
+ * batched mode; "cpu": the same ring and batch thread over the host build of
+ * the GPU decoder, no GPU needed; unset: the inflate thread pool).
  */
 #include <getopt.h>
 #include <time.h>
@@ -400,6 +404,79 @@ static int env_int(const char *name, int dflt)
     return v && *v ? atoi(v) : dflt;
 }
 
+/* ---- BAM readers ------------------------------------------------------------
+ * SS_BGZF_DEVICE unset: the reader's own inflate pool.  "1": the reader's
+ * batched mode over ss_inflate_members_host, one handle per reader on the
+ * first scoring device, slot memory page-locked.  "cpu": the batched mode over
+ * ss_inflate_members_cpu. */
+static int cb_inflate_device(void *user, const uint8_t *comp, const uint64_t *comp_off, uint32_t n, uint8_t *out,
+                             const uint64_t *out_off, uint32_t *status)
+{
+    return ss_inflate_members_host((ss_inflate_t *)user, comp, comp_off, n, out, out_off, status);
+}
+
+static int cb_inflate_cpu(void *user, const uint8_t *comp, const uint64_t *comp_off, uint32_t n, uint8_t *out,
+                          const uint64_t *out_off, uint32_t *status)
+{
+    (void)user;
+    return ss_inflate_members_cpu(comp, comp_off, n, out, out_off, status);
+}
+
+/* the first scoring device, as main() will parse it (errors are reported there) */
+static int first_device(void)
+{
+    const char *devs = getenv("SS_DEVICES");
+    if (devs && *devs) {
+        char *end;
+        const long v = strtol(devs, &end, 10);
+        if (end != devs && v >= 0 && v <= 1023) return (int)v;
+    }
+    return env_int("SS_DEVICE", 0);
+}
+
+/* seek: open at virtual offset voff (indexed files), else from the start */
+static bgzf_reader_t *reader_open(const char *path, int bthreads, int seek, uint64_t voff)
+{
+    const char *mode = getenv("SS_BGZF_DEVICE");
+    if (!mode || !*mode || !strcmp(mode, "0"))
+        return seek ? bgzf_open_at(path, bthreads, voff) : bgzf_open(path, bthreads);
+    int batch = env_int("SS_BGZF_DEVICE_BATCH", 256);
+    if (batch < 1) batch = 1;
+    if (batch > 4096) batch = 4096;
+    bgzf_batch_ops_t ops = {cb_inflate_cpu, NULL, NULL, NULL};
+    if (!strcmp(mode, "1")) {
+        ss_inflate_t *h = NULL;
+        const int rc = ss_inflate_create(first_device(), (uint32_t)batch, &h);
+        if (rc != SS_OK) {
+            fprintf(stderr, "[bam-somaticsniper] SS_BGZF_DEVICE=1: %s\n", ss_strerror(rc));
+            return NULL;
+        }
+        ops.inflate = cb_inflate_device;
+        ops.user = h;
+        ops.alloc = ss_host_alloc;
+        ops.release = ss_host_free;
+    } else if (strcmp(mode, "cpu")) {
+        fprintf(stderr, "[bam-somaticsniper] SS_BGZF_DEVICE='%s': expected 1 or cpu\n", mode);
+        return NULL;
+    }
+    bgzf_reader_t *r = bgzf_open_batched(path, seek ? voff : 0, batch, &ops);
+    if (!r && ops.user) ss_inflate_destroy((ss_inflate_t *)ops.user);
+    return r;
+}
+
+static void reader_close(bgzf_reader_t *r)
+{
+    uint64_t members = 0, batches = 0, fallback = 0;
+    void *user = NULL;
+    const int batched = bgzf_batch_stats(r, &members, &batches, &fallback, &user);
+    bgzf_close(r);
+    if (!batched) return;
+    if (timing)
+        fprintf(stderr, "bgzf device: %llu members in %llu batches, %llu re-inflated on the host\n",
+                (unsigned long long)members, (unsigned long long)batches, (unsigned long long)fallback);
+    if (user) ss_inflate_destroy((ss_inflate_t *)user);
+}
+
 /* SS_DEVICES: a comma list of distinct GPU indices (at most MAX_DEV).  An
  * empty, non-numeric, negative or repeated entry, or too many entries, is an
  * error: a typo must not silently put two scorers on one GPU.  Several
@@ -473,16 +550,16 @@ static void *group_main(void *arg)
     run_t *R = &g->R;
     run_scorers_start(R, g->sarg);
     if (g->v1 != UINT64_MAX && g->v2 != UINT64_MAX) {   /* a file without records here: no shared site */
-        bgzf_reader_t *f1 = bgzf_open_at(g->bam1, g->bthreads, g->v1);
-        bgzf_reader_t *f2 = bgzf_open_at(g->bam2, g->bthreads, g->v2);
+        bgzf_reader_t *f1 = reader_open(g->bam1, g->bthreads, 1, g->v1);
+        bgzf_reader_t *f2 = reader_open(g->bam2, g->bthreads, 1, g->v2);
         if (!f1 || !f2) {
             fprintf(stderr, "[bam-somaticsniper] cannot seek in the indexed BAMs\n");
             g->err = 1;
         } else if (dual_pileup_range(f1, f2, (int)SS_BAM_DEF_MASK, g->mapq, &g->s1, &g->s2, on_site, R)) {
             g->err = 1;
         }
-        if (f1) bgzf_close(f1);
-        if (f2) bgzf_close(f2);
+        if (f1) reader_close(f1);
+        if (f2) reader_close(f2);
     }
     run_scorers_finish(R);
     /* release the range's batches here, while other ranges still run (the
@@ -675,7 +752,7 @@ int main(int argc, char *argv[])
     fprintf(stderr, "Preparing to snipe some somatics\n");
     if (prm.use_priors) fprintf(stderr, "Using prior probabilities\n");
     const int bthreads = env_int("SS_BGZF_THREADS", 4);
-    bgzf_reader_t *fp1 = bgzf_open(argv[optind], bthreads);
+    bgzf_reader_t *fp1 = reader_open(argv[optind], bthreads, 0, 0);
     fprintf(stderr, "Normal bam is %s\n", argv[optind + 1]);
     fprintf(stderr, "Tumor bam is %s\n", argv[optind]);
     bam_header_t h1, h2;
@@ -683,7 +760,7 @@ int main(int argc, char *argv[])
         fprintf(stderr, "[bam-somaticsniper] cannot read BAM %s\n", argv[optind]);
         return 1;
     }
-    bgzf_reader_t *fp2 = bgzf_open(argv[optind + 1], bthreads);
+    bgzf_reader_t *fp2 = reader_open(argv[optind + 1], bthreads, 0, 0);
     if (!fp2 || bam_header_read(fp2, &h2)) {
         fprintf(stderr, "[bam-somaticsniper] cannot read BAM %s\n", argv[optind + 1]);
         return 1;
@@ -727,8 +804,8 @@ int main(int argc, char *argv[])
         stamp("pileup done");
         run_scorers_finish(&R);
     }
-    bgzf_close(fp1);
-    bgzf_close(fp2);
+    reader_close(fp1);
+    reader_close(fp2);
     bam_header_free(&h1);
     bam_header_free(&h2);
     fasta_index_free(R.fai);
