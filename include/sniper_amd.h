@@ -341,6 +341,119 @@ int  ss_inflate_check(ss_inflate_t *h);
 int  ss_bgzf_scan(const uint8_t *file, size_t len, uint64_t *comp_span, uint64_t *out_off,
                   uint32_t cap, uint32_t *n_members, size_t *consumed);
 
+/* ---- pileup columns from BAM records ----------------------------------------
+ * From uncompressed BAM alignment records (what ss_inflate_members_* leaves)
+ * to an ss_batch_t: the sites, entries and entry order of the CLI's column
+ * builder (cli/column_pileup.h, the reference's sniper_pileup.c walk), built
+ * on the GPU so that the batch can go straight into ss_score_batch_device.
+ *
+ * ss_pileup_plan (host) applies one sample's load rules and gives, per kept
+ * record in load order, its byte offset, the first position it contributes to
+ * and its contig.  The ss_pileup_*_device / _host / _cpu calls then build one
+ * region [lo, hi) of one contig for both samples; a site is a position where
+ * both samples have raw depth > 0 (deleted entries count, reference skips do
+ * not; the packed depth may be 0).
+ *
+ * Limits of one region call: hi - lo <= SS_PILEUP_MAX_SPAN positions, at most
+ * SS_PILEUP_MAX_RECORDS records and less than 4 GiB of record bytes per
+ * sample, at most SS_PILEUP_MAX_READS packed entries per sample (the CLI's own
+ * batch limit). */
+#define SS_PILEUP_MAX_SPAN    (1u << 22)
+#define SS_PILEUP_MAX_RECORDS ((1u << 24) - 1u)
+#define SS_PILEUP_MAX_READS   0xC0000000ull
+
+typedef struct ss_pileup ss_pileup_t;
+
+/* Walk state of ss_pileup_plan, carried from one chunk of a file to the next.
+ * has_prev == 0: no record yet (the walk is at contig 0, position 0). */
+typedef struct ss_pileup_state {
+    int32_t has_prev;
+    int32_t tid;          /* the walk's contig                              */
+    int64_t w;            /* the walk's position, a running maximum         */
+    int32_t max_tid;      /* highest contig of a kept-by-filter record      */
+    int32_t pad;
+} ss_pileup_state_t;
+
+/* One sample's records for a region call.  Record i starts (at its
+ * block_size field) at bytes[rec_off[i]]; from[i] must not decrease and must
+ * be >= the record's pos.  Records of one contig, in load order. */
+typedef struct ss_pileup_sample {
+    const uint8_t  *bytes;
+    uint64_t        n_bytes;
+    const uint64_t *rec_off;   /* [n] */
+    const int32_t  *from;      /* [n] */
+    uint32_t        n;
+    uint32_t        pad;
+} ss_pileup_sample_t;
+
+/* The columns of a region.  ref, off_t, off_n, reads_t, reads_n are exactly an
+ * ss_batch_t of n_sites sites.  The caller sets the pointers and capacities;
+ * ss_pileup_region_host / _cpu also write n_sites, n_reads_t, n_reads_n (the
+ * sizes needed, also when they return SS_E_CAPACITY) and n_invalid. */
+typedef struct ss_pileup_out {
+    uint64_t  cap_sites, cap_reads_t, cap_reads_n;
+    int32_t  *pos;        /* [cap_sites]   position of each site            */
+    uint8_t  *ref;        /* [cap_sites]   reference char, case kept        */
+    uint32_t *raw_t;      /* [cap_sites]   raw depth (deleted entries too)  */
+    uint32_t *raw_n;
+    uint32_t *off_t;      /* [cap_sites+1] */
+    uint32_t *off_n;
+    uint32_t *reads_t;    /* [cap_reads_t] packed entries, load order       */
+    uint32_t *reads_n;
+    uint64_t  n_sites, n_reads_t, n_reads_n;
+    uint64_t  n_invalid;  /* records that failed validation (both samples)  */
+} ss_pileup_out_t;
+
+int  ss_pileup_create(int device, ss_pileup_t **out);
+void ss_pileup_destroy(ss_pileup_t *h);
+/* Waits for the handle's work.  SS_E_INVAL if a record of a device call since
+ * the last check failed validation (clears it); debug build: SS_E_CORRUPT if a
+ * guard band around one of the handle's device buffers was overwritten. */
+int  ss_pileup_check(ss_pileup_t *h);
+
+/* Host only.  Walks bytes[0 .. len): whole BAM alignment records, positioned
+ * after the header.  A record is dropped if flag & mask is set (mask < 0:
+ * UNMAP | SECONDARY | QCFAIL | DUP, else UNMAP | mask) or mapq < thresh.  A
+ * kept record on a lower contig than one before it is SS_E_INVAL, as is a
+ * block_size below 32 or a CIGAR that passes its block.  For each record the
+ * walk keeps (end > W, cli/column_pileup.h) it stores the record's offset, its
+ * first contributing position and its contig; it stops after `cap` records or
+ * at the first incomplete record, and *consumed says where. */
+int  ss_pileup_plan(const uint8_t *bytes, size_t len, int mask, int thresh, ss_pileup_state_t *state,
+                    uint64_t *rec_off, int32_t *from, int32_t *tid, uint32_t cap, uint32_t *n,
+                    size_t *consumed);
+
+/* Pass 1, device pointers (the sample structs themselves are host memory):
+ * indexes and validates the records, counts every column of [lo, hi) and
+ * writes the totals to the three host u64s.  Runs on `stream` (a hipStream_t,
+ * NULL = default stream) and waits for it.  ref points at the contig's first
+ * base (ref[s] = pos < ref_len ? ref[pos] : 'N'; NULL: 'N' everywhere).
+ * Invalid records and a decreasing `from` are found on the device:
+ * ss_pileup_check reports SS_E_INVAL.  An invalid record contributes nothing
+ * and the other records' columns are complete.  After a decreasing `from` the
+ * record search is no longer exact: every access stays bounded, but which of
+ * the other records' entries reach a column is unspecified.  A sample's
+ * packed total above SS_PILEUP_MAX_READS is SS_E_CAPACITY.
+ * A handle's scratch buffers are shared by its calls: a call on another stream
+ * than the previous one first waits for that stream on the host. */
+int  ss_pileup_count_device(ss_pileup_t *h, const ss_pileup_sample_t *tumor, const ss_pileup_sample_t *normal,
+                            const uint8_t *ref, int64_t ref_len, int32_t lo, int32_t hi, uint64_t *n_sites,
+                            uint64_t *n_reads_t, uint64_t *n_reads_n, void *stream);
+/* Pass 2 of the latest ss_pileup_count_device (whose inputs must still be in
+ * place): fills out's device arrays, asynchronously on `stream`.
+ * SS_E_CAPACITY, with nothing stored, if a capacity is below the totals. */
+int  ss_pileup_fill_device(ss_pileup_t *h, const ss_pileup_out_t *out, void *stream);
+/* Host pointers: H2D, both passes, D2H, synchronous.  SS_E_INVAL with nothing
+ * stored for hi <= lo, a span above SS_PILEUP_MAX_SPAN, a decreasing `from`
+ * or a record offset outside bytes; SS_E_CAPACITY with the needed sizes in
+ * out and no array touched; SS_E_INVAL after the columns of the valid records
+ * were written if n_invalid records failed validation. */
+int  ss_pileup_region_host(ss_pileup_t *h, const ss_pileup_sample_t *tumor, const ss_pileup_sample_t *normal,
+                           const uint8_t *ref, int64_t ref_len, int32_t lo, int32_t hi, ss_pileup_out_t *out);
+/* The same core on the calling thread (no GPU): same codes, same arrays. */
+int  ss_pileup_region_cpu(const ss_pileup_sample_t *tumor, const ss_pileup_sample_t *normal,
+                          const uint8_t *ref, int64_t ref_len, int32_t lo, int32_t hi, ss_pileup_out_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@ __all__ = [
     "Params", "Synth", "Batch", "Context", "SniperError", "library_path", "load_library",
     "synth_batch_host", "model_check", "pack_read", "SS_GLF_DTYPE", "SS_CALL_DTYPE", "EXPORTED_SYMBOLS",
     "Inflater", "bgzf_scan", "inflate_cpu",
+    "Pileup", "PileupState", "PileupRegion", "pileup_plan", "pileup_region_cpu",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "ss_host_alloc", "ss_host_free",
     "ss_inflate_create", "ss_inflate_destroy", "ss_inflate_members_device", "ss_inflate_members_host",
     "ss_inflate_members_cpu", "ss_inflate_check", "ss_bgzf_scan",
+    "ss_pileup_create", "ss_pileup_destroy", "ss_pileup_check", "ss_pileup_plan", "ss_pileup_count_device",
+    "ss_pileup_fill_device", "ss_pileup_region_host", "ss_pileup_region_cpu",
 )
 
 
@@ -257,6 +260,17 @@ def load_library():
     lib.ss_inflate_members_host.argtypes = [vp, vp, vp, u32, vp, vp, vp]
     lib.ss_inflate_members_cpu.argtypes = [vp, vp, u32, vp, vp, vp]
     lib.ss_bgzf_scan.argtypes = [vp, C.c_size_t, vp, vp, u32, C.POINTER(u32), C.POINTER(C.c_size_t)]
+    lib.ss_pileup_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.ss_pileup_destroy.argtypes = [vp]
+    lib.ss_pileup_destroy.restype = None
+    lib.ss_pileup_check.argtypes = [vp]
+    lib.ss_pileup_plan.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, vp, vp, u32, C.POINTER(u32),
+                                   C.POINTER(C.c_size_t)]
+    lib.ss_pileup_count_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(u64),
+                                           C.POINTER(u64), C.POINTER(u64), vp]
+    lib.ss_pileup_fill_device.argtypes = [vp, vp, vp]
+    lib.ss_pileup_region_host.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
+    lib.ss_pileup_region_cpu.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
     if hasattr(lib, "ss__test_poke_table"):         # test hook, not in the public header
         lib.ss__test_poke_table.argtypes = [vp, u64, C.c_int]
     if hasattr(lib, "ss__test_route_counts"):       # test hook, not in the public header
@@ -586,3 +600,218 @@ class Inflater:
     def check(self):
         """Wait for the handle's stream; debug build: SS_E_CORRUPT if a guard band was overwritten."""
         _check(self.lib.ss_inflate_check(self.h), "ss_inflate_check")
+
+
+# --------------------------------------------------------------------------- pileup from BAM records
+SS_PILEUP_MAX_SPAN = 1 << 22
+
+
+class PileupState(C.Structure):
+    """ss_pileup_state_t -- the walk state pileup_plan carries from chunk to chunk."""
+    _fields_ = [("has_prev", C.c_int32), ("tid", C.c_int32), ("w", C.c_int64), ("max_tid", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class _PileupSample(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("n_bytes", C.c_uint64), ("rec_off", C.c_void_p), ("from_", C.c_void_p),
+                ("n", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class _PileupOut(C.Structure):
+    _fields_ = [("cap_sites", C.c_uint64), ("cap_reads_t", C.c_uint64), ("cap_reads_n", C.c_uint64),
+                ("pos", C.c_void_p), ("ref", C.c_void_p), ("raw_t", C.c_void_p), ("raw_n", C.c_void_p),
+                ("off_t", C.c_void_p), ("off_n", C.c_void_p), ("reads_t", C.c_void_p), ("reads_n", C.c_void_p),
+                ("n_sites", C.c_uint64), ("n_reads_t", C.c_uint64), ("n_reads_n", C.c_uint64),
+                ("n_invalid", C.c_uint64)]
+
+
+@dataclass
+class PileupRegion:
+    """The columns of one region: `batch` (what Context.score_batch takes) plus each
+    site's position and raw depths.  rc is SS_OK, or SS_E_INVAL when n_invalid
+    records failed validation (the other records' columns are all here)."""
+    batch: Batch
+    pos: np.ndarray          # i32 [n]
+    raw_t: np.ndarray        # u32 [n]
+    raw_n: np.ndarray        # u32 [n]
+    rc: int = 0
+    n_invalid: int = 0
+
+
+def pileup_plan(data, mask: int = -1, thresh: int = 0, state: PileupState | None = None, cap: int | None = None):
+    """ss_pileup_plan over uncompressed BAM record bytes (positioned after the
+    header): (rec_off u64, from i32, tid i32, consumed).  `state` (a PileupState,
+    updated in place) lets a file be planned in consecutive chunks; `cap` bounds
+    the records kept by one call."""
+    lib = load_library()
+    a = _u8(data)
+    if state is None:
+        state = PileupState()
+    if cap is None:
+        cap = a.size // 36 + 1                     # no record is shorter than 36 bytes
+    off = np.zeros(cap, np.uint64)
+    frm = np.zeros(cap, np.int32)
+    tid = np.zeros(cap, np.int32)
+    n, used = C.c_uint32(), C.c_size_t()
+    _check(lib.ss_pileup_plan(_ptr(a) or None, a.size, mask, thresh, C.byref(state), off.ctypes.data,
+                              frm.ctypes.data, tid.ctypes.data, cap, C.byref(n), C.byref(used)), "ss_pileup_plan")
+    k = n.value
+    return off[:k].copy(), frm[:k].copy(), tid[:k].copy(), int(used.value)
+
+
+def _pileup_sample(sample):
+    """(bytes, rec_off, from) as numpy arrays -> (_PileupSample, arrays kept alive)."""
+    data, off, frm = sample
+    a = _u8(data)
+    off = np.ascontiguousarray(off, np.uint64)
+    frm = np.ascontiguousarray(frm, np.int32)
+    if off.shape != frm.shape or off.ndim != 1:
+        raise ValueError("rec_off and from must be 1-d arrays of one length")
+    return _PileupSample(_ptr(a) or None, a.size, _ptr(off) or None, _ptr(frm) or None, off.size, 0), (a, off, frm)
+
+
+def _pileup_region(call, what, tumor, normal, ref, lo, hi, caps, invalid_ok):
+    st, keep_t = _pileup_sample(tumor)
+    sn, keep_n = _pileup_sample(normal)
+    r = None if ref is None else _u8(ref)
+    ref_len = 0 if r is None else r.size
+    out = _PileupOut()
+    arrays = None
+    for attempt in range(2):
+        ns, nt, nn = caps if caps is not None else (0, 0, 0)
+        arrays = (np.zeros(ns, np.int32), np.zeros(ns, np.uint8), np.zeros(ns, np.uint32), np.zeros(ns, np.uint32),
+                  np.zeros(ns + 1, np.uint32), np.zeros(ns + 1, np.uint32), np.zeros(nt, np.uint32),
+                  np.zeros(nn, np.uint32))
+        out = _PileupOut(ns, nt, nn, *(a.ctypes.data for a in arrays))
+        rc = call(C.byref(st), C.byref(sn), None if r is None else (_ptr(r) or None), ref_len, lo, hi, C.byref(out))
+        if rc == SS_E_CAPACITY and caps is None and max(out.n_reads_t, out.n_reads_n) <= 0xC0000000:
+            caps = (int(out.n_sites), int(out.n_reads_t), int(out.n_reads_n))      # the sizes needed
+            continue
+        break
+    if rc != SS_OK and not (rc == SS_E_INVAL and invalid_ok and out.n_invalid):
+        raise SniperError(rc, what)
+    ns, nt, nn = int(out.n_sites), int(out.n_reads_t), int(out.n_reads_n)
+    pos, refc, raw_t, raw_n, off_t, off_n, reads_t, reads_n = arrays
+    return PileupRegion(Batch(refc[:ns], off_t[:ns + 1], off_n[:ns + 1], reads_t[:nt], reads_n[:nn]), pos[:ns],
+                        raw_t[:ns], raw_n[:ns], rc, int(out.n_invalid))
+
+
+def pileup_region_cpu(tumor, normal, ref, lo: int, hi: int, caps=None, invalid_ok: bool = False) -> PileupRegion:
+    """ss_pileup_region_cpu: the columns of [lo, hi) built by the shared core on the
+    calling thread (no GPU).  tumor / normal: (bytes, rec_off, from) of one contig's
+    records in load order (pileup_plan); ref: the contig's bases (bytes / u8 array)
+    or None.  caps: (sites, reads_t, reads_n) capacities (default: sized by a first
+    call).  invalid_ok: return the columns (rc == SS_E_INVAL) when records failed
+    validation instead of raising."""
+    lib = load_library()
+    return _pileup_region(lib.ss_pileup_region_cpu, "ss_pileup_region_cpu", tumor, normal, ref, lo, hi, caps,
+                          invalid_ok)
+
+
+class Pileup:
+    """Pileup columns from BAM records on the GPU (ss_pileup_t)."""
+
+    def __init__(self, device: int = 0):
+        self.lib = load_library()
+        h = C.c_void_p()
+        _check(self.lib.ss_pileup_create(device, C.byref(h)), "ss_pileup_create")
+        self.h = h
+        self.device = device
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.ss_pileup_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @staticmethod
+    def _p(x):
+        if x is None:
+            return None
+        return x if isinstance(x, int) else x.data_ptr()
+
+    def count(self, tumor, normal, ref, ref_len: int, lo: int, hi: int, stream=None):
+        """ss_pileup_count_device.  tumor / normal: (bytes, n_bytes, rec_off, from, n)
+        of torch CUDA tensors or raw device addresses; ref: a tensor / address or
+        None.  Synchronous; returns (n_sites, n_reads_t, n_reads_n)."""
+        p = self._p
+        smp = [_PileupSample(p(b), nb, p(o), p(f), n, 0) for b, nb, o, f, n in (tumor, normal)]
+        ns, nt, nn = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        sh = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        _check(self.lib.ss_pileup_count_device(self.h, C.byref(smp[0]), C.byref(smp[1]), p(ref), ref_len, lo, hi,
+                                               C.byref(ns), C.byref(nt), C.byref(nn), sh), "ss_pileup_count_device")
+        return int(ns.value), int(nt.value), int(nn.value)
+
+    def fill(self, pos, ref, raw_t, raw_n, off_t, off_n, reads_t, reads_n, cap_sites: int, cap_reads_t: int,
+             cap_reads_n: int, stream=None):
+        """ss_pileup_fill_device into torch CUDA tensors (or raw device addresses),
+        asynchronous on `stream`."""
+        p = self._p
+        out = _PileupOut(cap_sites, cap_reads_t, cap_reads_n, p(pos), p(ref), p(raw_t), p(raw_n), p(off_t), p(off_n),
+                         p(reads_t), p(reads_n))
+        sh = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        _check(self.lib.ss_pileup_fill_device(self.h, C.byref(out), sh), "ss_pileup_fill_device")
+
+    def region(self, tumor, normal, ref, lo: int, hi: int, caps=None, invalid_ok: bool = False) -> PileupRegion:
+        """ss_pileup_region_host: numpy in, numpy out; arguments and result as
+        pileup_region_cpu."""
+        return _pileup_region(lambda *a: self.lib.ss_pileup_region_host(self.h, *a), "ss_pileup_region_host", tumor,
+                              normal, ref, lo, hi, caps, invalid_ok)
+
+    def region_device(self, tumor, normal, ref, lo: int, hi: int, stream=None):
+        """Records (numpy, as for `region`) to the device, both passes there, and the
+        batch stays in HBM: returns the dict of torch tensors Context.score_device
+        takes (ref, off_tumor, off_normal, reads_tumor, reads_normal, n_sites) plus
+        pos, raw_t, raw_n.  The fill is asynchronous on `stream`."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        smp = []
+        for data, off, frm in (tumor, normal):
+            a = _u8(data)
+            off = np.ascontiguousarray(off, np.uint64)
+            # only the bytes the records lie in: from the lowest offset to the end of the last block
+            b0 = min(int(off.min()), a.size) if off.size else 0
+            b1 = a.size
+            last = int(off.max()) if off.size else 0
+            if off.size and last + 4 <= a.size:
+                block = int.from_bytes(a[last:last + 4].tobytes(), "little", signed=True)
+                if 0 <= block <= a.size - last - 4:
+                    b1 = last + 4 + block
+            b1 = max(b0, b1)
+            part = a[b0:b1] if b1 > b0 else np.zeros(1, np.uint8)
+            d_bytes = torch.from_numpy(part if part.flags.writeable else part.copy()).to(dev)   # no host copy if it can be avoided
+            d_off = torch.from_numpy((off - np.uint64(b0)).astype(np.int64)).to(dev)
+            d_from = torch.from_numpy(np.ascontiguousarray(frm, np.int32).copy()).to(dev)
+            smp.append((d_bytes, b1 - b0, d_off, d_from, int(off.size)))
+        r = None if ref is None else _u8(ref)
+        d_ref = None if r is None or r.size == 0 else torch.from_numpy(r.copy()).to(dev)
+        torch.cuda.synchronize(dev)
+        ns, nt, nn = self.count(smp[0], smp[1], d_ref, 0 if r is None else r.size, lo, hi, stream=stream)
+        i32 = dict(dtype=torch.int32, device=dev)
+        out = {"pos": torch.empty(max(1, ns), **i32), "ref": torch.empty(max(1, ns), dtype=torch.uint8, device=dev),
+               "raw_t": torch.empty(max(1, ns), **i32), "raw_n": torch.empty(max(1, ns), **i32),
+               "off_tumor": torch.empty(ns + 1, **i32), "off_normal": torch.empty(ns + 1, **i32),
+               "reads_tumor": torch.empty(max(1, nt), **i32), "reads_normal": torch.empty(max(1, nn), **i32)}
+        torch.cuda.synchronize(dev)
+        self.fill(out["pos"], out["ref"], out["raw_t"], out["raw_n"], out["off_tumor"], out["off_normal"],
+                  out["reads_tumor"], out["reads_normal"], ns, nt, nn, stream=stream)
+        out["n_sites"] = ns
+        out["n_reads"] = (nt, nn)
+        out["_inputs"] = (smp, d_ref)          # the fill reads them: kept until the caller drops the dict
+        return out
+
+    def check(self):
+        """Wait for the handle's work; SS_E_INVAL if a record of a device call failed
+        validation; debug build: SS_E_CORRUPT if a guard band was overwritten."""
+        _check(self.lib.ss_pileup_check(self.h), "ss_pileup_check")

@@ -99,11 +99,11 @@ extern "C" const char *ss_strerror(int code)
 {
     switch (code) {
     case SS_OK: return "ok";
-    case SS_E_INVAL: return "invalid argument or malformed batch";
+    case SS_E_INVAL: return "invalid argument, malformed batch or invalid BAM record";
     case SS_E_HIP: return "HIP runtime error";
     case SS_E_NOMEM: return "out of memory";
     case SS_E_TABLES: return "model tables differ from the reference (libm mismatch), or the device copy no longer matches the host's";
-    case SS_E_CAPACITY: return "capacity exceeded (emitted calls, work lists or pileup depth)";
+    case SS_E_CAPACITY: return "capacity exceeded (emitted calls, work lists, pileup depth or a pileup region's sites / entries)";
     case SS_E_NODEV: return "no usable HIP device";
     case SS_E_CORRUPT: return "device memory outside a buffer was overwritten (debug guard bands)";
     default: return "unknown error";
