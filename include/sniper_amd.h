@@ -454,6 +454,62 @@ int  ss_pileup_region_host(ss_pileup_t *h, const ss_pileup_sample_t *tumor, cons
 int  ss_pileup_region_cpu(const ss_pileup_sample_t *tumor, const ss_pileup_sample_t *normal,
                           const uint8_t *ref, int64_t ref_len, int32_t lo, int32_t hi, ss_pileup_out_t *out);
 
+/* ---- the planner on the device ----------------------------------------------
+ * ss_pileup_plan_device gives what ss_pileup_plan gives, from record bytes that
+ * lie in device memory (what ss_inflate_members_device leaves), so that
+ * inflate -> plan -> pileup -> score needs no inflated byte on the host.  The
+ * record chain is serial; the bytes are cut into chunks of SS_PLAN_CHUNK that
+ * guess their entry, walk in parallel and are stitched exactly (DESIGN.md
+ * section 14).  The outcome does not depend on the guesses. */
+#define SS_PLAN_CHUNK 16384u     /* bytes per chunk of the device walk */
+#define SS_BAM_MORE   1          /* ss_bam_header_scan: the prefix ends inside the header */
+
+/* Why a record chain ended (ss_pileup_split_cpu). */
+#define SS_PLAN_END_DATA  1      /* fewer than 4 bytes left, or a record the bytes do not hold whole */
+#define SS_PLAN_END_BLOCK 2      /* a block_size below 32 */
+
+/* Consecutive kept records of one contig: rec_off[first .. first + n). */
+typedef struct ss_pileup_run {
+    int32_t  tid;
+    uint32_t first, n;
+    int32_t  lo, hi;      /* lowest `from`, highest reference end of the run */
+} ss_pileup_run_t;
+
+/* ss_pileup_plan over device bytes: bytes, rec_off, from and tid are device
+ * memory ([cap] each), everything else host memory.  Same filter, same rules,
+ * same stops as ss_pileup_plan: for the same bytes, mask, thresh, in-state
+ * and cap it stores the same arrays, *n, *consumed and out-state and returns
+ * the same code; after SS_E_INVAL the arrays, *n and the state are those of
+ * the records before the failing one and *consumed is its offset.  Nothing
+ * is stored at or past rec_off[*n].  n_ref (ss_bam_header_scan; <= 0: not
+ * known) only sharpens the guesses.
+ * runs[0 .. *n_runs) groups the kept records by contig, so that a caller can
+ * hand rec_off + first and from + first to ss_pileup_count_device without
+ * fetching the arrays.  More than cap_runs runs is SS_E_CAPACITY with the
+ * count needed in *n_runs and runs untouched; the arrays, *n, *consumed and
+ * the state are stored as otherwise.  *n_repaired (may be NULL): chunks whose
+ * guess was wrong and that were walked again.
+ * Runs on `stream` and waits for it, as ss_pileup_count_device does.  One
+ * call takes fewer than 2^31 records. */
+int  ss_pileup_plan_device(ss_pileup_t *h, const uint8_t *bytes, uint64_t len, int32_t n_ref, int mask,
+                           int thresh, ss_pileup_state_t *state, uint64_t *rec_off, int32_t *from, int32_t *tid,
+                           uint32_t cap, uint32_t *n, uint64_t *consumed, ss_pileup_run_t *runs,
+                           uint32_t cap_runs, uint32_t *n_runs, uint32_t *n_repaired, void *stream);
+/* Host only: the same guess, walk, stitch and repair on the calling thread,
+ * with chunks of `chunk` bytes (>= 1).  Stores the offset of every whole
+ * record of the chain from bytes[0] in rec_off ([cap]; more records than cap
+ * is SS_E_CAPACITY with the count in *n and the first cap offsets stored),
+ * where the chain ended in *end_at and why in *end_why (SS_PLAN_END_*), and
+ * the chunks walked again in *n_repaired.  The offsets do not depend on
+ * `chunk` or n_ref. */
+int  ss_pileup_split_cpu(const uint8_t *bytes, uint64_t len, int32_t n_ref, uint32_t chunk, uint64_t *rec_off,
+                         uint64_t cap, uint64_t *n, uint64_t *end_at, int *end_why, uint32_t *n_repaired);
+/* Host only: parses the magic, l_text and the reference list of uncompressed
+ * BAM bytes.  SS_OK with the reference count in *n_ref and the offset of the
+ * first record in *records_at; SS_BAM_MORE, with nothing stored, if the bytes
+ * end inside the header; SS_E_INVAL on a bad magic or a negative length. */
+int  ss_bam_header_scan(const uint8_t *bytes, size_t len, int32_t *n_ref, size_t *records_at);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "ss_inflate_members_cpu", "ss_inflate_check", "ss_bgzf_scan",
     "ss_pileup_create", "ss_pileup_destroy", "ss_pileup_check", "ss_pileup_plan", "ss_pileup_count_device",
     "ss_pileup_fill_device", "ss_pileup_region_host", "ss_pileup_region_cpu",
+    "ss_pileup_plan_device", "ss_pileup_split_cpu", "ss_bam_header_scan",
 )
 
 
@@ -271,8 +272,16 @@ def load_library():
     lib.ss_pileup_fill_device.argtypes = [vp, vp, vp]
     lib.ss_pileup_region_host.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
     lib.ss_pileup_region_cpu.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
+    lib.ss_pileup_plan_device.argtypes = [vp, vp, u64, C.c_int32, C.c_int, C.c_int, vp, vp, vp, vp, u32,
+                                          C.POINTER(u32), C.POINTER(u64), vp, u32, C.POINTER(u32), C.POINTER(u32), vp]
+    lib.ss_pileup_split_cpu.argtypes = [vp, u64, C.c_int32, u32, vp, u64, C.POINTER(u64), C.POINTER(u64),
+                                        C.POINTER(C.c_int), C.POINTER(u32)]
+    lib.ss_bam_header_scan.argtypes = [vp, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)]
     if hasattr(lib, "ss__test_poke_table"):         # test hook, not in the public header
         lib.ss__test_poke_table.argtypes = [vp, u64, C.c_int]
+    if hasattr(lib, "ss__plan_phase_ms"):           # measurement hook, not in the public header
+        lib.ss__plan_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        lib.ss__plan_phase_ms.restype = None
     if hasattr(lib, "ss__test_route_counts"):       # test hook, not in the public header
         lib.ss__test_route_counts.argtypes = [vp, C.POINTER(C.c_uint32)]
     if lib.ss_abi_version() != 1:
@@ -604,6 +613,10 @@ class Inflater:
 
 # --------------------------------------------------------------------------- pileup from BAM records
 SS_PILEUP_MAX_SPAN = 1 << 22
+SS_PLAN_CHUNK = 16384                            # bytes per chunk of the device planner's walk
+SS_BAM_MORE = 1                                  # bam_header_scan: the prefix ends inside the header
+SS_PLAN_END_DATA, SS_PLAN_END_BLOCK = 1, 2       # why a record chain ended (pileup_split_cpu)
+SS_RUN_DTYPE = np.dtype([("tid", "<i4"), ("first", "<u4"), ("n", "<u4"), ("lo", "<i4"), ("hi", "<i4")])   # ss_pileup_run_t
 
 
 class PileupState(C.Structure):
@@ -657,6 +670,34 @@ def pileup_plan(data, mask: int = -1, thresh: int = 0, state: PileupState | None
                               frm.ctypes.data, tid.ctypes.data, cap, C.byref(n), C.byref(used)), "ss_pileup_plan")
     k = n.value
     return off[:k].copy(), frm[:k].copy(), tid[:k].copy(), int(used.value)
+
+
+def pileup_split_cpu(data, n_ref: int = 0, chunk: int = SS_PLAN_CHUNK, cap: int | None = None):
+    """ss_pileup_split_cpu: the device planner's guess / walk / stitch / repair on the
+    calling thread with chunks of `chunk` bytes.  Returns (rec_off u64 of every whole
+    record of the chain, end_at, end_why (SS_PLAN_END_*), n_repaired)."""
+    lib = load_library()
+    a = _u8(data)
+    if cap is None:
+        cap = a.size // 36 + 1                     # no record is shorter than 36 bytes
+    off = np.zeros(cap, np.uint64)
+    n, end_at, why, rep = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint32()
+    _check(lib.ss_pileup_split_cpu(_ptr(a) or None, a.size, n_ref, chunk, _ptr(off) or None, cap, C.byref(n),
+                                   C.byref(end_at), C.byref(why), C.byref(rep)), "ss_pileup_split_cpu")
+    return off[: n.value].copy(), int(end_at.value), int(why.value), int(rep.value)
+
+
+def bam_header_scan(data):
+    """ss_bam_header_scan over a prefix of uncompressed BAM bytes: (n_ref, records_at),
+    or None if the prefix ends inside the header."""
+    lib = load_library()
+    a = _u8(data)
+    n_ref, at = C.c_int32(), C.c_size_t()
+    rc = lib.ss_bam_header_scan(_ptr(a) or None, a.size, C.byref(n_ref), C.byref(at))
+    if rc == SS_BAM_MORE:
+        return None
+    _check(rc, "ss_bam_header_scan")
+    return int(n_ref.value), int(at.value)
 
 
 def _pileup_sample(sample):
@@ -810,6 +851,46 @@ class Pileup:
         out["n_reads"] = (nt, nn)
         out["_inputs"] = (smp, d_ref)          # the fill reads them: kept until the caller drops the dict
         return out
+
+    def plan_device(self, data, n_bytes: int, n_ref: int, mask: int = -1, thresh: int = 0,
+                    state: PileupState | None = None, cap: int | None = None, stream=None, cap_runs: int | None = None,
+                    invalid_ok: bool = False):
+        """ss_pileup_plan_device: pileup_plan over record bytes in device memory (a torch
+        CUDA u8 tensor or a raw address, positioned after the header).  Returns
+        (rec_off i64, from_ i32, tid i32 torch tensors trimmed to n, consumed, runs
+        (SS_RUN_DTYPE), n_repaired); `state` is updated in place.  invalid_ok: after
+        SS_E_INVAL return the records before the failing one (the code is then in
+        self.last_plan_rc) instead of raising."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if state is None:
+            state = PileupState()
+        if cap is None:
+            cap = n_bytes // 36 + 1                # no record is shorter than 36 bytes
+        if cap_runs is None:
+            cap_runs = max(1, n_ref) + 16
+        off = torch.empty(max(1, cap), dtype=torch.int64, device=dev)
+        frm = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+        tid = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        sh = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        n, used, n_runs, rep = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+        for attempt in range(2):
+            runs = np.zeros(cap_runs, SS_RUN_DTYPE)
+            st = PileupState.from_buffer_copy(state)
+            rc = self.lib.ss_pileup_plan_device(self.h, self._p(data), n_bytes, n_ref, mask, thresh, C.byref(st),
+                                                off.data_ptr(), frm.data_ptr(), tid.data_ptr(), cap, C.byref(n),
+                                                C.byref(used), runs.ctypes.data, cap_runs, C.byref(n_runs),
+                                                C.byref(rep), sh)
+            if rc != SS_E_CAPACITY or attempt:
+                break
+            cap_runs = int(n_runs.value)           # the count needed
+        self.last_plan_rc = rc
+        if rc != SS_OK and not (rc == SS_E_INVAL and invalid_ok):
+            raise SniperError(rc, "ss_pileup_plan_device")
+        C.memmove(C.byref(state), C.byref(st), C.sizeof(st))
+        k = int(n.value)
+        return off[:k], frm[:k], tid[:k], int(used.value), runs[: n_runs.value].copy(), int(rep.value)
 
     def check(self):
         """Wait for the handle's work; SS_E_INVAL if a record of a device call failed

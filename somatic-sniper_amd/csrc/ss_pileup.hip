@@ -2,6 +2,8 @@
  * ss_pileup.hip -- pileup columns from BAM records on the GPU
  * (include/sniper_amd.h, "pileup columns from BAM records"): the kernels, the
  * ss_pileup_t handle and the device / host entry points.  DESIGN.md section 13.
+ * The planner on the device (ss_pileup_plan_device) is
+ * the last part of this file, with its own notes.
  *
  * One call builds one region [lo, hi) of one contig for both samples:
  *   ss_pileup_index   one lane per record: validates it (ss_pileup_core.h) and
@@ -28,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,8 +38,13 @@
 
 #include "sniper_amd.h"
 #include "ss_pileup_core.h"
+#include "ss_plan_core.h"
 
 extern "C" int ssp_sample_args_ok(const ss_pileup_sample_t *s);     /* ss_pileup_plan.c */
+typedef int (*ssp_rewalk_fn)(void *ctx, uint32_t k, uint64_t entry, ssp_chunk_t *c);
+extern "C" int ssp_plan_stitch(ssp_chunk_t *c, uint32_t n_chunks, uint64_t chunk, uint64_t len, ssp_rewalk_fn rewalk,
+                               void *ctx, uint64_t *n_rec, uint64_t *end_at, uint32_t *end_status,
+                               uint32_t *n_repaired);                /* ss_pileup_plan.c */
 
 struct ssp_max_op {
     __host__ __device__ int32_t operator()(int32_t a, int32_t b) const { return a > b ? a : b; }
@@ -236,6 +244,9 @@ enum {
     /* staging of ss_pileup_region_host */
     B_BYTES_T, B_BYTES_N, B_OFF_T, B_OFF_N, B_FROM_T, B_FROM_N, B_REF,
     B_OPOS, B_OREF, B_ORAW_T, B_ORAW_N, B_OOFF_T, B_OOFF_N, B_OREADS_T, B_OREADS_N,
+    /* ss_pileup_plan_device: the chunk table, the kept chunks, one entry per record, the result, the runs */
+    B_PCHUNK, B_PEMIT, B_POFF, B_PTID, B_PBEG, B_PEND, B_PFLAG, B_PSEG, B_PMAXT, B_PRANK, B_PFROM, B_PRUNV, B_PRES,
+    B_PRUNK, B_PRUNA, B_PNRUN,
     B_COUNT
 };
 
@@ -253,6 +264,7 @@ struct ss_pileup {
     int64_t ref_pos0, ref_len;
     int32_t lo, hi;
     uint64_t tot[3];
+    double plan_ms[3];           /* the latest ss_pileup_plan_device: guess + walk, stitch, emit + plan (host clock) */
 };
 
 #define HIPCHK(x)                                   \
@@ -618,4 +630,432 @@ extern "C" int ss_pileup_region_host(ss_pileup_t *h, const ss_pileup_sample_t *t
     HIPCHK(hipStreamSynchronize(s));
     h->counted = 0;              /* the staged inputs may be replaced by the next call */
     return bad ? SS_E_INVAL : SS_OK;
+}
+
+/* ------------------------------------------------------- the planner ---- */
+/*
+ * ss_pileup_plan_device:
+ *   ss_plan_walk   one workgroup per chunk of SS_PLAN_CHUNK bytes: stages the
+ *                  chunk into LDS with coalesced loads, guesses its entry (256
+ *                  offsets tested at a time, the lowest accepted one wins: the
+ *                  serial ssp_guess), then one lane chases the chain through
+ *                  LDS and writes the chunk's ssp_chunk_t;
+ *   the stitch     on the host over the chunk table (24 bytes a chunk), the
+ *                  function the CPU twin runs; a wrong guess launches
+ *                  ss_plan_walk again for that one chunk from its true entry;
+ *   ss_plan_emit   one workgroup per kept chunk: the walk again, now noting the
+ *                  offsets in LDS, then one thread per record decodes the head
+ *                  and the CIGAR end (ssp_plan_record) and writes the record's
+ *                  scan elements;
+ *   two hipCUB scans (the walk state, the running maximum contig), ss_plan_keep
+ *   (load rules per record, first error by atomicMin on a scratch word),
+ *   a hipCUB sum (ranks), ss_plan_out (compaction in order), ss_plan_final
+ *   (one thread: n, consumed, code, out-state) and a hipCUB reduce-by-key for
+ *   the runs.
+ * No atomic touches an output array; the one on the scratch word is a minimum,
+ * so every result is the same from run to run.
+ *
+ * Bounds.  The window is staged with every global load inside bytes[0 .. len);
+ * ssp_walk reads a block_size only where 4 bytes are left; a record is decoded
+ * only after the walk found it whole; record-indexed stores are below n_rec,
+ * stores to the caller's arrays below cap.
+ */
+#define SSP_PLAN_WIN (SS_PLAN_CHUNK + 48u)      /* the chunk, 4 bytes past it, alignment slack */
+#define SSP_PLAN_REL (SS_PLAN_CHUNK / 36u + 2u) /* no record is shorter than 36 bytes */
+
+struct ssp_emit_t {
+    uint64_t entry;
+    uint32_t chunk, base;        /* the chunk's number; the index of its first record */
+};
+
+struct ssp_runv_t {
+    int32_t lo, hi;
+    uint32_t n;
+};
+
+typedef ssp_plan_res_t ssp_plan_res;     /* ss_plan_core.h; first_err and cut are set to SSP_NO_RECORD before the kernels run */
+
+struct ssp_seg_op {
+    __host__ __device__ ssp_seg_t operator()(const ssp_seg_t &a, const ssp_seg_t &b) const { return ssp_seg_join(a, b); }
+};
+struct ssp_runv_op {
+    __host__ __device__ ssp_runv_t operator()(const ssp_runv_t &a, const ssp_runv_t &b) const
+    {
+        ssp_runv_t r;
+        r.lo = a.lo < b.lo ? a.lo : b.lo;
+        r.hi = a.hi > b.hi ? a.hi : b.hi;
+        r.n = a.n + b.n;
+        return r;
+    }
+};
+
+/* Stages bytes[start .. start + want) into s; byte x then lies at
+ * s[a + x - start], a (returned) being the misalignment of byte `start`.
+ * 16-byte granules that lie whole inside the span go as one vector load, the
+ * two ragged ones byte by byte. */
+static __device__ __forceinline__ uint32_t ssp_stage(const uint8_t *__restrict__ bytes, uint64_t start, uint32_t want,
+                                                     uint8_t *s)
+{
+    const uint8_t *g0 = bytes + start;
+    const uint32_t a = (uint32_t)((uintptr_t)g0 & 15u);
+    const uint32_t n_gran = (a + want + 15u) / 16u;
+    for (uint32_t g = threadIdx.x; g < n_gran; g += 256u) {
+        const int32_t lo = (int32_t)(16u * g) - (int32_t)a;             /* relative to start */
+        if (lo >= 0 && (uint32_t)lo + 16u <= want) {
+            *(uint4 *)(s + 16u * g) = *(const uint4 *)(g0 + lo);
+        } else {
+            for (int32_t j = 0; j < 16; ++j)
+                if (lo + j >= 0 && (uint32_t)(lo + j) < want) s[16u * g + (uint32_t)j] = g0[lo + j];
+        }
+    }
+    __syncthreads();
+    return a;
+}
+
+static __device__ __forceinline__ uint32_t ssp_plan_want(uint64_t len, uint64_t start)
+{
+    return len - start < (uint64_t)SS_PLAN_CHUNK + 4u ? (uint32_t)(len - start) : SS_PLAN_CHUNK + 4u;
+}
+
+/* Chunk first + blockIdx.x.  forced == SSP_NO_GUESS: the chunk guesses its
+ * entry (chunk 0 enters at 0); else it enters at `forced` (a repair). */
+__global__ __launch_bounds__(256) void ss_plan_walk(const uint8_t *__restrict__ bytes, uint64_t len, int32_t n_ref,
+                                                    uint32_t first, uint64_t forced, ssp_chunk_t *__restrict__ table)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[SSP_PLAN_WIN];
+    __shared__ uint32_t s_first[4];
+    const uint32_t k = first + blockIdx.x;
+    const uint64_t start = (uint64_t)k * SS_PLAN_CHUNK;
+    if (start >= len) return;
+    const uint64_t end = len - start < SS_PLAN_CHUNK ? len : start + SS_PLAN_CHUNK;
+    const uint32_t a = ssp_stage(bytes, start, ssp_plan_want(len, start), s_win);
+    uint64_t entry = forced;
+    if (forced == SSP_NO_GUESS && k == 0u) entry = 0;
+    if (forced == SSP_NO_GUESS && k != 0u) {
+        const uint32_t span = (uint32_t)(end - start), lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        for (uint32_t base = 0; base < span; base += 256u) {
+            const uint32_t o = base + threadIdx.x;
+            const bool ok = o < span && ssp_guess_ok(bytes, len, start + o, n_ref);
+            const unsigned long long hit = __ballot(ok);
+            if (lane == 0u) s_first[wave] = hit ? base + 64u * wave + (uint32_t)__ffsll((long long)hit) - 1u : 0xffffffffu;
+            __syncthreads();
+            uint32_t m = 0xffffffffu;
+            for (int w = 0; w < 4; ++w) m = s_first[w] < m ? s_first[w] : m;
+            __syncthreads();
+            if (m != 0xffffffffu) {
+                entry = start + m;
+                break;
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        ssp_chunk_t c;
+        c.entry = entry;
+        c.exit = entry;
+        c.count = 0;
+        c.status = SSP_WALK_EXIT;
+        if (entry != SSP_NO_GUESS && entry >= start && entry <= len)
+            c.status = ssp_walk(s_win + a, start, len, start, entry, end, nullptr, 0, &c.exit, &c.count);
+        table[k] = c;
+    }
+}
+
+__global__ __launch_bounds__(256) void ss_plan_emit(const uint8_t *__restrict__ bytes, uint64_t len,
+                                                    const ssp_emit_t *__restrict__ list, uint32_t flag_mask,
+                                                    int mapq_thresh, uint32_t n_rec, uint64_t *__restrict__ off,
+                                                    int32_t *__restrict__ tid, int32_t *__restrict__ beg,
+                                                    int32_t *__restrict__ rend, uint32_t *__restrict__ flag,
+                                                    ssp_seg_t *__restrict__ seg, int32_t *__restrict__ maxt)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[SSP_PLAN_WIN];
+    __shared__ uint32_t s_rel[SSP_PLAN_REL];
+    __shared__ uint32_t s_count;
+    const ssp_emit_t e = list[blockIdx.x];
+    const uint64_t start = (uint64_t)e.chunk * SS_PLAN_CHUNK;
+    if (start >= len || e.entry < start || e.entry > len) return;
+    const uint64_t end = len - start < SS_PLAN_CHUNK ? len : start + SS_PLAN_CHUNK;
+    const uint32_t a = ssp_stage(bytes, start, ssp_plan_want(len, start), s_win);
+    if (threadIdx.x == 0) {
+        uint64_t exit_at;
+        uint32_t count;
+        (void)ssp_walk(s_win + a, start, len, start, e.entry, end, s_rel, SSP_PLAN_REL, &exit_at, &count);
+        s_count = count < SSP_PLAN_REL ? count : SSP_PLAN_REL;
+    }
+    __syncthreads();
+    const uint32_t count = s_count;
+    for (uint32_t i = threadIdx.x; i < count; i += 256u) {
+        const uint64_t idx = (uint64_t)e.base + i;
+        if (idx >= n_rec) continue;
+        const uint64_t at = start + s_rel[i];                  /* a whole record: the walk checked it against len */
+        int32_t t, b, en;
+        const uint32_t fl = ssp_plan_record(bytes + at, flag_mask, mapq_thresh, &t, &b, &en);
+        off[idx] = at;
+        tid[idx] = t;
+        beg[idx] = b;
+        rend[idx] = en;
+        flag[idx] = fl;
+        seg[idx] = ssp_seg_of(fl, t, b);
+        maxt[idx] = ssp_maxt_of(fl, t);
+    }
+}
+
+/* seg and maxt hold the inclusive scans.  One thread per record, plus one that
+ * writes the closing 0 of the flags the rank sum runs over. */
+__global__ __launch_bounds__(256) void ss_plan_keep(uint32_t n_rec, int32_t t0, int64_t w0, int32_t max0,
+                                                    const int32_t *__restrict__ tid, const int32_t *__restrict__ beg,
+                                                    const int32_t *__restrict__ rend,
+                                                    const uint32_t *__restrict__ flag,
+                                                    const ssp_seg_t *__restrict__ seg,
+                                                    const int32_t *__restrict__ maxt, uint32_t *__restrict__ keep,
+                                                    int32_t *__restrict__ from, ssp_plan_res *__restrict__ res)
+{
+    const uint64_t i64 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i64 > n_rec) return;
+    const uint32_t i = (uint32_t)i64;
+    if (i == n_rec) {
+        keep[i] = 0u;
+        return;
+    }
+    uint32_t k;
+    int32_t f;
+    if (ssp_plan_rules(flag[i], tid[i], beg[i], rend[i], i ? seg[i - 1u] : ssp_seg_none(),
+                       i ? maxt[i - 1u] : INT32_MIN, t0, w0, max0, &k, &f))
+        atomicMin(&res->first_err, i);
+    keep[i] = k;
+    from[i] = f;
+}
+
+/* rank[i]: kept records before record i (rank[n_rec]: all). */
+__global__ __launch_bounds__(256) void ss_plan_out(uint32_t n_rec, uint32_t cap, const uint64_t *__restrict__ off,
+                                                   const int32_t *__restrict__ tid, const int32_t *__restrict__ rend,
+                                                   const uint32_t *__restrict__ rank,
+                                                   const int32_t *__restrict__ from, uint64_t *__restrict__ o_off,
+                                                   int32_t *__restrict__ o_from, int32_t *__restrict__ o_tid,
+                                                   ssp_runv_t *__restrict__ runv, ssp_plan_res *__restrict__ res)
+{
+    const uint64_t i64 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i64 >= n_rec) return;
+    const uint32_t i = (uint32_t)i64, r = rank[i];
+    if (rank[i + 1u] == r || i >= res->first_err || r >= cap) return;
+    o_off[r] = off[i];
+    o_from[r] = from[i];
+    o_tid[r] = tid[i];
+    ssp_runv_t v;
+    v.lo = from[i];
+    v.hi = rend[i];
+    v.n = 1u;
+    runv[r] = v;
+    if (r == cap - 1u) res->cut = i;                     /* the cap-th kept record: one writer */
+}
+
+__global__ void ss_plan_final(const uint8_t *__restrict__ bytes, uint32_t n_rec, int32_t t0, int64_t w0, int32_t max0,
+                              uint64_t chain_end, uint32_t chain_bad, const uint64_t *__restrict__ off,
+                              const uint32_t *__restrict__ rank, const ssp_seg_t *__restrict__ seg,
+                              const int32_t *__restrict__ maxt, ssp_plan_res *__restrict__ res)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    ssp_plan_finish(bytes, n_rec, t0, w0, max0, chain_end, (int)chain_bad, off, rank, seg, maxt, res);
+}
+
+struct ssp_repair_ctx {
+    const uint8_t *bytes;
+    uint64_t len;
+    int32_t n_ref;
+    ssp_chunk_t *table;
+    hipStream_t s;
+};
+
+static int plan_rewalk(void *ctx, uint32_t k, uint64_t entry, ssp_chunk_t *c)
+{
+    const ssp_repair_ctx *r = (const ssp_repair_ctx *)ctx;
+    hipLaunchKernelGGL(ss_plan_walk, dim3(1), dim3(256), 0, r->s, r->bytes, r->len, r->n_ref, k, entry, r->table);
+    if (int rc = launched()) return rc;
+    HIPCHK(hipMemcpyAsync(c, r->table + k, sizeof *c, hipMemcpyDeviceToHost, r->s));
+    HIPCHK(hipStreamSynchronize(r->s));
+    return SS_OK;
+}
+
+extern "C" int ss_pileup_plan_device(ss_pileup_t *h, const uint8_t *bytes, uint64_t len, int32_t n_ref, int mask,
+                                     int thresh, ss_pileup_state_t *state, uint64_t *rec_off, int32_t *from,
+                                     int32_t *tid, uint32_t cap, uint32_t *n, uint64_t *consumed,
+                                     ss_pileup_run_t *runs, uint32_t cap_runs, uint32_t *n_runs,
+                                     uint32_t *n_repaired, void *stream)
+{
+    if (!h || (!bytes && len) || !state || !n || !n_runs || (cap && (!rec_off || !from || !tid)) ||
+        (cap_runs && !runs))
+        return SS_E_INVAL;
+    const uint64_t nc64 = (len + SS_PLAN_CHUNK - 1u) / SS_PLAN_CHUNK;
+    if (nc64 > 0x7fffffffull) return SS_E_INVAL;
+    HIPCHK(hipSetDevice(h->device));
+    const uint32_t flag_mask = mask < 0 ? (4u | 256u | 512u | 1024u) : (4u | (uint32_t)mask);   /* as ss_pileup_plan */
+    const int mapq_thresh = thresh < 0 ? 0 : thresh;
+    const int32_t t0 = state->has_prev ? state->tid : 0, max0 = state->has_prev ? state->max_tid : -1;
+    const int64_t w0 = state->has_prev ? state->w : 0;
+    hipStream_t s = (hipStream_t)stream;
+    *n = 0;
+    *n_runs = 0;
+    if (n_repaired) *n_repaired = 0;
+    ssp_plan_res res;
+    memset(&res, 0, sizeof res);
+    res.code = SS_OK;
+    res.tid = t0;
+    res.w = w0;
+    res.max_tid = max0;
+    uint64_t n_rec = 0, chain_end = 0;
+    uint32_t chain_st = SSP_WALK_END;
+    void *p;
+    int rc;
+    typedef std::chrono::steady_clock clk;
+    const clk::time_point c0 = clk::now();
+    clk::time_point c1 = c0, c2 = c0;
+    if (cap && len >= 4u) {                               /* else ss_pileup_plan's loop does not run either */
+        const uint32_t n_chunks = (uint32_t)nc64;
+        if ((rc = buf_ensure(h, B_PCHUNK, (size_t)n_chunks * sizeof(ssp_chunk_t), &p))) return rc;
+        ssp_chunk_t *table = (ssp_chunk_t *)p;
+        if (h->last != s) HIPCHK(hipStreamSynchronize(h->last));   /* the scratch buffers are shared between calls */
+        h->last = s;
+        hipLaunchKernelGGL(ss_plan_walk, dim3(n_chunks), dim3(256), 0, s, bytes, len, n_ref, 0u, SSP_NO_GUESS, table);
+        if ((rc = launched())) return rc;
+        std::vector<ssp_chunk_t> tab(n_chunks);
+        HIPCHK(hipMemcpyAsync(tab.data(), table, (size_t)n_chunks * sizeof(ssp_chunk_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        c1 = clk::now();
+        ssp_repair_ctx rx = {bytes, len, n_ref, table, s};
+        uint32_t rep = 0;
+        if ((rc = ssp_plan_stitch(tab.data(), n_chunks, SS_PLAN_CHUNK, len, plan_rewalk, &rx, &n_rec, &chain_end,
+                                  &chain_st, &rep)))
+            return rc;
+        c2 = clk::now();
+        if (n_repaired) *n_repaired = rep;
+        if (n_rec > 0x7fffffffull) return SS_E_INVAL;
+        res.consumed = chain_end;
+        res.code = chain_st == SSP_WALK_BAD ? SS_E_INVAL : SS_OK;
+        if (n_rec) {
+            const uint32_t R = (uint32_t)n_rec;
+            std::vector<ssp_emit_t> list;
+            uint32_t base = 0;
+            for (uint32_t k = 0; k < n_chunks; ++k) {
+                if (tab[k].status == SSP_WALK_SKIP || !tab[k].count) continue;
+                list.push_back(ssp_emit_t{tab[k].entry, k, base});
+                base += tab[k].count;
+            }
+            const size_t n1 = (size_t)R + 1;
+            const uint32_t n_out = R < cap ? R : cap;
+            if ((rc = buf_ensure(h, B_PEMIT, list.size() * sizeof(ssp_emit_t), &p))) return rc;
+            ssp_emit_t *d_list = (ssp_emit_t *)p;
+            if ((rc = buf_ensure(h, B_POFF, n1 * sizeof(uint64_t), &p))) return rc;
+            uint64_t *d_off = (uint64_t *)p;
+            if ((rc = buf_ensure(h, B_PTID, n1 * sizeof(int32_t), &p))) return rc;
+            int32_t *d_tid = (int32_t *)p;
+            if ((rc = buf_ensure(h, B_PBEG, n1 * sizeof(int32_t), &p))) return rc;
+            int32_t *d_beg = (int32_t *)p;
+            if ((rc = buf_ensure(h, B_PEND, n1 * sizeof(int32_t), &p))) return rc;
+            int32_t *d_end = (int32_t *)p;
+            if ((rc = buf_ensure(h, B_PFLAG, n1 * sizeof(uint32_t), &p))) return rc;
+            uint32_t *d_flag = (uint32_t *)p;
+            if ((rc = buf_ensure(h, B_PSEG, n1 * sizeof(ssp_seg_t), &p))) return rc;
+            ssp_seg_t *d_seg = (ssp_seg_t *)p;
+            if ((rc = buf_ensure(h, B_PMAXT, n1 * sizeof(int32_t), &p))) return rc;
+            int32_t *d_maxt = (int32_t *)p;
+            if ((rc = buf_ensure(h, B_PRANK, n1 * sizeof(uint32_t), &p))) return rc;
+            uint32_t *d_rank = (uint32_t *)p;
+            if ((rc = buf_ensure(h, B_PFROM, n1 * sizeof(int32_t), &p))) return rc;
+            int32_t *d_from = (int32_t *)p;
+            if ((rc = buf_ensure(h, B_PRUNV, ((size_t)n_out + 1) * sizeof(ssp_runv_t), &p))) return rc;
+            ssp_runv_t *d_runv = (ssp_runv_t *)p;
+            if ((rc = buf_ensure(h, B_PRUNK, ((size_t)n_out + 1) * sizeof(int32_t), &p))) return rc;
+            int32_t *d_runk = (int32_t *)p;
+            if ((rc = buf_ensure(h, B_PRUNA, ((size_t)n_out + 1) * sizeof(ssp_runv_t), &p))) return rc;
+            ssp_runv_t *d_runa = (ssp_runv_t *)p;
+            if ((rc = buf_ensure(h, B_PNRUN, sizeof(uint32_t), &p))) return rc;
+            uint32_t *d_nrun = (uint32_t *)p;
+            if ((rc = buf_ensure(h, B_PRES, sizeof(ssp_plan_res), &p))) return rc;
+            ssp_plan_res *d_res = (ssp_plan_res *)p;
+            size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+            HIPCHK(hipcub::DeviceScan::InclusiveScan(nullptr, t1, d_seg, d_seg, ssp_seg_op(), (int)R, s));
+            HIPCHK(hipcub::DeviceScan::InclusiveScan(nullptr, t2, d_maxt, d_maxt, ssp_max_op(), (int)R, s));
+            HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, d_rank, d_rank, (int)n1, s));
+            HIPCHK(hipcub::DeviceReduce::ReduceByKey(nullptr, t4, tid, d_runk, d_runv, d_runa, d_nrun, ssp_runv_op(),
+                                                     (int)n_out, s));
+            size_t tmp = t1 > t2 ? t1 : t2;
+            tmp = tmp > t3 ? tmp : t3;
+            tmp = tmp > t4 ? tmp : t4;
+            if ((rc = buf_ensure(h, B_SCAN, tmp ? tmp : 1, &p))) return rc;
+            void *d_tmp = p;
+            tmp = h->buf[B_SCAN].bytes;
+            HIPCHK(hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(ssp_emit_t), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemsetAsync(d_res, 0xff, sizeof(ssp_plan_res), s));
+            hipLaunchKernelGGL(ss_plan_emit, dim3((uint32_t)list.size()), dim3(256), 0, s, bytes, len,
+                               (const ssp_emit_t *)d_list, flag_mask, mapq_thresh, R, d_off, d_tid, d_beg, d_end,
+                               d_flag, d_seg, d_maxt);
+            if ((rc = launched())) return rc;
+            size_t tb = tmp;
+            HIPCHK(hipcub::DeviceScan::InclusiveScan(d_tmp, tb, d_seg, d_seg, ssp_seg_op(), (int)R, s));
+            tb = tmp;
+            HIPCHK(hipcub::DeviceScan::InclusiveScan(d_tmp, tb, d_maxt, d_maxt, ssp_max_op(), (int)R, s));
+            const uint32_t blocks = (uint32_t)((n1 + 255u) / 256u);
+            hipLaunchKernelGGL(ss_plan_keep, dim3(blocks), dim3(256), 0, s, R, t0, w0, max0, (const int32_t *)d_tid,
+                               (const int32_t *)d_beg, (const int32_t *)d_end, (const uint32_t *)d_flag,
+                               (const ssp_seg_t *)d_seg, (const int32_t *)d_maxt, d_rank, d_from, d_res);
+            if ((rc = launched())) return rc;
+            tb = tmp;
+            HIPCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_rank, d_rank, (int)n1, s));
+            hipLaunchKernelGGL(ss_plan_out, dim3(blocks), dim3(256), 0, s, R, cap, (const uint64_t *)d_off,
+                               (const int32_t *)d_tid, (const int32_t *)d_end, (const uint32_t *)d_rank,
+                               (const int32_t *)d_from, rec_off, from, tid, d_runv, d_res);
+            if ((rc = launched())) return rc;
+            hipLaunchKernelGGL(ss_plan_final, dim3(1), dim3(64), 0, s, bytes, R, t0, w0, max0, chain_end,
+                               chain_st == SSP_WALK_BAD ? 1u : 0u, (const uint64_t *)d_off, (const uint32_t *)d_rank,
+                               (const ssp_seg_t *)d_seg, (const int32_t *)d_maxt, d_res);
+            if ((rc = launched())) return rc;
+            HIPCHK(hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (res.n > n_out) return SS_E_HIP;           /* cannot happen: the ranks are below cap and n_rec */
+            if (res.n) {
+                uint32_t nrun = 0;
+                tb = tmp;
+                HIPCHK(hipcub::DeviceReduce::ReduceByKey(d_tmp, tb, tid, d_runk, d_runv, d_runa, d_nrun, ssp_runv_op(),
+                                                         (int)res.n, s));
+                HIPCHK(hipMemcpyAsync(&nrun, d_nrun, sizeof nrun, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                *n_runs = nrun;
+                if (nrun <= cap_runs) {
+                    std::vector<int32_t> rk(nrun);
+                    std::vector<ssp_runv_t> ra(nrun);
+                    HIPCHK(hipMemcpyAsync(rk.data(), d_runk, (size_t)nrun * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                    HIPCHK(hipMemcpyAsync(ra.data(), d_runa, (size_t)nrun * sizeof(ssp_runv_t), hipMemcpyDeviceToHost,
+                                          s));
+                    HIPCHK(hipStreamSynchronize(s));
+                    uint32_t first = 0;
+                    for (uint32_t i = 0; i < nrun; ++i) {
+                        runs[i].tid = rk[i];
+                        runs[i].first = first;
+                        runs[i].n = ra[i].n;
+                        runs[i].lo = ra[i].lo;
+                        runs[i].hi = ra[i].hi;
+                        first += ra[i].n;
+                    }
+                }
+            }
+        }
+    }
+    h->plan_ms[0] = std::chrono::duration<double, std::milli>(c1 - c0).count();
+    h->plan_ms[1] = std::chrono::duration<double, std::milli>(c2 - c1).count();
+    h->plan_ms[2] = std::chrono::duration<double, std::milli>(clk::now() - c2).count();
+    state->has_prev = 1;
+    state->tid = res.tid;
+    state->w = res.w;
+    state->max_tid = res.max_tid;
+    *n = res.n;
+    if (consumed) *consumed = res.consumed;
+    if (*n_runs > cap_runs) return SS_E_CAPACITY;
+    return res.code;
+}
+
+/* measurement hook (tools/plan_bench.py), not in the public header: the phases
+ * of the latest ss_pileup_plan_device.  Each phase ends at a point where the
+ * call waits for the stream anyway, so the host clock brackets it. */
+extern "C" void ss__plan_phase_ms(ss_pileup_t *h, double ms[3])
+{
+    for (int k = 0; k < 3; ++k) ms[k] = h ? h->plan_ms[k] : 0.0;
 }
